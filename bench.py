@@ -51,7 +51,49 @@ def parse_args():
                         "cross_barrier.py): optimizer applies as each "
                         "bucket's communication lands; the next forward "
                         "blocks per-layer on its params")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step "
+                        "computed (loss, sampled params and grads) as "
+                        "DIR/<name>.npy; the last timed step starts from "
+                        "the seeded initial weights (restored untimed)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
+
+
+# Outputs larger than this many elements are dumped as a fixed, seeded
+# sample (2**22 float32 = 16 MiB per array).
+DUMP_MAX_ELEMS = 1 << 22
+DUMP_SEED = 0
+
+
+def _sample_flat(tensors, n_max: int) -> "torch.Tensor":
+    """Concatenate tensors flat as float32 and, if longer than n_max, take
+    a sample at sorted indices drawn from a fixed seed (same indices for
+    the same model on every run)."""
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    if flat.numel() > n_max:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randint(flat.numel(), (n_max,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.cpu()
+
+
+def dump_outputs(out_dir: str, loss, net) -> None:
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for p in net.parameters() if p.requires_grad]
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu(),
+        "params": _sample_flat(params, DUMP_MAX_ELEMS),
+        "grads": _sample_flat(
+            [p.grad if p.grad is not None else torch.zeros_like(p)
+             for p in params], DUMP_MAX_ELEMS),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.numpy().astype(np.float32))
 
 
 def build(args, device):
@@ -149,6 +191,8 @@ def main():
     if on_gpu:
         torch.backends.cudnn.benchmark = True
 
+    # fixed seed: weights and synthetic inputs are identical run to run
+    torch.manual_seed(DUMP_SEED)
     net, step_fn, per_step_items, unit, batch = build(args, device)
 
     cparams = None
@@ -191,6 +235,27 @@ def main():
         except Exception as e:
             print("tunableop load failed: %s" % e, file=sys.stderr)
 
+    # --dump-outputs: snapshot the seeded initial state before any step.
+    # One step reproduces to rounding, but SGD (lr 0.1, one repeated
+    # batch) amplifies the nondeterministic conv-backward rounding ~10x per
+    # step, so the state after the warmup and timed steps differs
+    # run to run far beyond rounding.  The last timed step is therefore run
+    # from this snapshot (restored outside the timed window).
+    state_tensors = list(net.parameters()) + list(net.buffers())
+    init_state = [t.detach().clone() for t in state_tensors] \
+        if args.dump_outputs else None
+
+    def restore_initial_state():
+        with torch.no_grad():
+            for t, s in zip(state_tensors, init_state):
+                t.copy_(s)
+            # in place, so a captured graph keeps its buffer addresses;
+            # a zero momentum buffer makes the next step a first SGD step
+            for st in opt.state.values():
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+
     use_bf16 = args.dtype == "bf16" and on_gpu
     autocast = torch.autocast("cuda", dtype=torch.bfloat16) if use_bf16 \
         else torch.autocast("cpu", enabled=False)
@@ -212,6 +277,7 @@ def main():
 
     # -- hipGraph capture ---------------------------------------------------
     graphed = None
+    graphed_loss = None
     # auto: capture at N=1 (well-tested, removes launch gaps); stay eager
     # at N>1 — collectives already overlap via async works and the capture
     # gain measured ~0.3% against real replay risk on an untested topology
@@ -228,7 +294,7 @@ def main():
                 dist.barrier()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                train_step()
+                graphed_loss = train_step()
             graphed = g
         except Exception as e:
             if rank == 0:
@@ -247,8 +313,8 @@ def main():
     def run_step():
         if graphed is not None:
             graphed.replay()
-        else:
-            train_step()
+            return graphed_loss
+        return train_step()
 
     for _ in range(max(args.warmup, 1)):
         run_step()
@@ -258,8 +324,18 @@ def main():
     if on_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        run_step()
+    for i in range(args.steps):
+        if init_state is not None and i == args.steps - 1:
+            if cb is not None:
+                cb.synchronize()
+            if on_gpu:
+                torch.cuda.synchronize()
+            pause = time.perf_counter()
+            restore_initial_state()
+            if on_gpu:
+                torch.cuda.synchronize()
+            t0 += time.perf_counter() - pause   # restore is not timed
+        loss = run_step()
     if cb is not None:
         cb.synchronize()          # drain in-flight per-bucket updates
     if on_gpu:
@@ -304,6 +380,8 @@ def main():
             },
         }
         print(json.dumps(out))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, loss, net)
     if cb is not None:
         cb.stop()
     bps.shutdown()

@@ -104,3 +104,35 @@ def test_bench_torchrun_eight_ranks():
     out = _check_json(lines[0], 8)
     assert out["config"]["parallelism"] == "dp8"
     assert out["config"]["global_batch"] == 8 * 64
+
+
+def _dump(tmp_path, name, steps):
+    out_dir = tmp_path / name
+    r = subprocess.run(
+        [sys.executable, "bench.py", "--model", "mlp", "--steps", str(steps),
+         "--warmup", "1", "--device", "cpu", "--dump-outputs", str(out_dir)],
+        cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
+    assert _check_json(line, 1)["steps"] == steps
+    return out_dir
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's results as float
+    .npy files.  That step starts from the seeded initial weights, so the
+    same arguments give identical outputs, whatever --steps is."""
+    import numpy as np
+    a = _dump(tmp_path, "a", 2)
+    b = _dump(tmp_path, "b", 2)
+    c = _dump(tmp_path, "c", 3)
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["grads.npy", "loss.npy", "params.npy"]
+    assert sum(p.stat().st_size for p in a.iterdir()) <= 64 * 2**20
+    for n in names:
+        x = np.load(a / n)
+        assert x.dtype in (np.float32, np.float64)
+        assert np.isfinite(x).all()
+        assert np.array_equal(x, np.load(b / n)), n
+        assert np.array_equal(x, np.load(c / n)), n
+    assert np.abs(np.load(a / "grads.npy")).max() > 0
