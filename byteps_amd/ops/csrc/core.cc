@@ -64,23 +64,21 @@ int bps_fp8_decompress(const void* code, int64_t n, const void* amax,
                        void* out, void* stream);
 
 // -- fused batchnorm (bn.hip) ----------------------------------------------
-int bps_bn_reduce(const void* x, long long M, int C, void* sums,
-                  void* stream);
-int bps_bn_finalize(const void* sums, long long M, int C, float eps,
-                    float momentum, void* mean_out, void* invstd_out,
-                    void* running_mean, void* running_var, int update_running,
-                    void* stream);
+int bps_bn_ticket_words(void);
+long long bps_bn_stats_ws_floats(long long M, int C, int bwd);
+int bps_bn_fwd_stats(const void* x, long long M, int C, float eps,
+                     float momentum, void* mean_out, void* invstd_out,
+                     void* running_mean, void* running_var,
+                     int update_running, void* ws, void* tickets,
+                     void* stream);
 int bps_bn_fwd_apply(const void* x, const void* res, void* y, long long M,
                      int C, const void* mean, const void* invstd,
                      const void* gamma, const void* beta, int relu,
                      void* mask, void* stream);
-int bps_bn_bwd_reduce(const void* x, const void* dy, const void* mask,
-                      long long M, int C, const void* mean,
-                      const void* invstd, void* partial, int relu,
-                      void* stream);
-int bps_bn_fold(const void* partial, long long M, int C, void* sums2,
-                void* stream);
-int bps_bn_red_blocks(void);
+int bps_bn_bwd_stats(const void* x, const void* dy, const void* mask,
+                     long long M, int C, const void* mean,
+                     const void* invstd, void* sums2, int relu, void* ws,
+                     void* tickets, void* stream);
 
 // -- fused layernorm (ln.hip) ----------------------------------------------
 int bps_ln_supported(int C);
@@ -288,22 +286,20 @@ PYBIND11_MODULE(_core, m) {
         });
 
   // fused batchnorm
-  m.attr("BN_RED_BLOCKS") = bps_bn_red_blocks();
-  m.def("bn_reduce", [](uintptr_t x, int64_t M, int C, uintptr_t sums,
-                        uintptr_t s) {
-    check(bps_bn_reduce(CP(x), M, C, P(sums), P(s)), "bps_bn_reduce");
+  m.attr("BN_TICKET_WORDS") = bps_bn_ticket_words();
+  m.def("bn_stats_ws", [](int64_t M, int C, int bwd) {
+    long long n = bps_bn_stats_ws_floats(M, C, bwd);
+    if (n < 0) throw std::runtime_error("bn_stats_ws: unsupported C");
+    return n;
   });
-  m.def("bn_fold", [](uintptr_t partial, int64_t M, int C, uintptr_t sums2,
-                      uintptr_t s) {
-    check(bps_bn_fold(CP(partial), M, C, P(sums2), P(s)), "bps_bn_fold");
-  });
-  m.def("bn_finalize",
-        [](uintptr_t sums, int64_t M, int C, float eps, float momentum,
+  m.def("bn_fwd_stats",
+        [](uintptr_t x, int64_t M, int C, float eps, float momentum,
            uintptr_t mean, uintptr_t invstd, uintptr_t rmean, uintptr_t rvar,
-           int upd, uintptr_t s) {
-          check(bps_bn_finalize(CP(sums), M, C, eps, momentum, P(mean),
-                                P(invstd), P(rmean), P(rvar), upd, P(s)),
-                "bps_bn_finalize");
+           int upd, uintptr_t ws, uintptr_t tickets, uintptr_t s) {
+          check(bps_bn_fwd_stats(CP(x), M, C, eps, momentum, P(mean),
+                                 P(invstd), P(rmean), P(rvar), upd, P(ws),
+                                 P(tickets), P(s)),
+                "bps_bn_fwd_stats");
         });
   m.def("bn_fwd_apply",
         [](uintptr_t x, uintptr_t res, uintptr_t y, int64_t M, int C,
@@ -314,13 +310,14 @@ PYBIND11_MODULE(_core, m) {
                                  P(mask), P(s)),
                 "bps_bn_fwd_apply");
         });
-  m.def("bn_bwd_reduce",
-        [](uintptr_t x, uintptr_t dy, uintptr_t y, int64_t M, int C,
+  m.def("bn_bwd_stats",
+        [](uintptr_t x, uintptr_t dy, uintptr_t mask, int64_t M, int C,
            uintptr_t mean, uintptr_t invstd, uintptr_t sums2, int relu,
-           uintptr_t s) {
-          check(bps_bn_bwd_reduce(CP(x), CP(dy), CP(y), M, C, CP(mean),
-                                  CP(invstd), P(sums2), relu, P(s)),
-                "bps_bn_bwd_reduce");
+           uintptr_t ws, uintptr_t tickets, uintptr_t s) {
+          check(bps_bn_bwd_stats(CP(x), CP(dy), CP(mask), M, C, CP(mean),
+                                 CP(invstd), P(sums2), relu, P(ws),
+                                 P(tickets), P(s)),
+                "bps_bn_bwd_stats");
         });
   m.def("bn_bwd_apply",
         [](uintptr_t x, uintptr_t dy, uintptr_t y, uintptr_t dx,

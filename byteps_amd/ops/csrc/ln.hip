@@ -123,7 +123,7 @@ __global__ void ln_fwd_kernel(const bf16* __restrict__ x,
 // bwd: dx = invstd * (dyg - mean(dyg) - xhat * mean(dyg*xhat)) with
 // dyg = dy*gamma; also accumulates per-block column partials for
 // dbeta = Σ_rows dy and dgamma = Σ_rows dy*xhat (transposed layout
-// [row][LN_RED_BLOCKS], folded by bps_bn_fold-style kernel).
+// [row][LN_RED_BLOCKS], folded by bps_ln_fold).
 // ---------------------------------------------------------------------------
 
 __global__ void ln_bwd_kernel(const bf16* __restrict__ x,
@@ -219,7 +219,7 @@ __device__ inline float wave_row_sum_ln(const float* __restrict__ row,
   return acc;
 }
 
-// adaptive grid matching bn.hip's red_grid (stride stays LN_RED_BLOCKS)
+// adaptive grid with a work cap (stride stays LN_RED_BLOCKS)
 inline int ln_red_grid(long long M, int C) {
   int groups = BLOCK / (C >> 3);
   if (groups < 1) groups = 1;

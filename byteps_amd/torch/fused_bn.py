@@ -36,7 +36,7 @@ def _nhwc_ok(x: torch.Tensor, C: int) -> bool:
 class _FusedBNFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var,
-                momentum, eps, relu, training):
+                momentum, eps, relu, training, tickets):
         N, C, H, W = x.shape
         M = N * H * W
         core = K.core()
@@ -44,16 +44,14 @@ class _FusedBNFunction(torch.autograd.Function):
         s = _stream(x)
         y = torch.empty_like(x)
         if training:
-            nb = core.BN_RED_BLOCKS
-            partial = torch.empty(nb * 2 * C, dtype=torch.float32,
-                                  device=dev)
-            core.bn_reduce(x.data_ptr(), M, C, partial.data_ptr(), s)
+            ws = torch.empty(core.bn_stats_ws(M, C, 0), dtype=torch.float32,
+                             device=dev)
             mean = torch.empty(C, dtype=torch.float32, device=dev)
             invstd = torch.empty(C, dtype=torch.float32, device=dev)
-            core.bn_finalize(partial.data_ptr(), M, C, eps, momentum,
-                             mean.data_ptr(), invstd.data_ptr(),
-                             running_mean.data_ptr(), running_var.data_ptr(),
-                             1, s)
+            core.bn_fwd_stats(x.data_ptr(), M, C, eps, momentum,
+                              mean.data_ptr(), invstd.data_ptr(),
+                              running_mean.data_ptr(), running_var.data_ptr(),
+                              1, ws.data_ptr(), tickets.data_ptr(), s)
         else:
             mean = running_mean.float()
             invstd = torch.rsqrt(running_var.float() + eps)
@@ -73,6 +71,7 @@ class _FusedBNFunction(torch.autograd.Function):
         ctx.relu = relu
         ctx.has_res = residual is not None
         ctx.dims = (M, C)
+        ctx.tickets = tickets
         return y
 
     @staticmethod
@@ -82,15 +81,16 @@ class _FusedBNFunction(torch.autograd.Function):
         core = K.core()
         dy = dy.contiguous(memory_format=torch.channels_last)
         s = _stream(x)
-        nb = core.BN_RED_BLOCKS
         mask_ptr = mask.data_ptr() if ctx.relu else 0
-        partial = torch.empty(nb * 2 * C, dtype=torch.float32,
-                              device=x.device)
-        core.bn_bwd_reduce(x.data_ptr(), dy.data_ptr(), mask_ptr, M, C,
-                           mean.data_ptr(), invstd.data_ptr(),
-                           partial.data_ptr(), int(ctx.relu), s)
+        ws = torch.empty(core.bn_stats_ws(M, C, 1), dtype=torch.float32,
+                         device=x.device)
         sums2 = torch.empty(2 * C, dtype=torch.float32, device=x.device)
-        core.bn_fold(partial.data_ptr(), M, C, sums2.data_ptr(), s)
+        # the second half of the module's counters belongs to backward
+        bwd_tickets = ctx.tickets.data_ptr() + 4 * core.BN_TICKET_WORDS
+        core.bn_bwd_stats(x.data_ptr(), dy.data_ptr(), mask_ptr, M, C,
+                          mean.data_ptr(), invstd.data_ptr(),
+                          sums2.data_ptr(), int(ctx.relu), ws.data_ptr(),
+                          bwd_tickets, s)
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if ctx.has_res else None
         core.bn_bwd_apply(x.data_ptr(), dy.data_ptr(), mask_ptr,
@@ -100,7 +100,8 @@ class _FusedBNFunction(torch.autograd.Function):
                           sums2.data_ptr(), int(ctx.relu), s)
         dbeta = sums2[:C]
         dgamma = sums2[C:]
-        return (dx, dres, dgamma, dbeta, None, None, None, None, None, None)
+        return (dx, dres, dgamma, dbeta, None, None, None, None, None, None,
+                None)
 
 
 class FusedBNReLU(nn.Module):
@@ -127,6 +128,19 @@ class FusedBNReLU(nn.Module):
         # and the per-call long-add kernel showed up in profiles
         self.register_buffer("num_batches_tracked",
                              torch.tensor(0, dtype=torch.long))
+        # arrival counters of the statistics kernels (forward half, then
+        # backward half).  Zeroed once here and left at zero by every
+        # launch, so a call needs no fill kernel.  A plain attribute, not a
+        # buffer: buffer broadcasts and state_dict must never touch it.
+        self._stat_tickets: Optional[torch.Tensor] = None
+
+    def _tickets(self, dev: torch.device) -> torch.Tensor:
+        t = self._stat_tickets
+        if t is None or t.device != dev:
+            t = torch.zeros(2 * K.core().BN_TICKET_WORDS, dtype=torch.int32,
+                            device=dev)
+            self._stat_tickets = t
+        return t
 
     def forward(self, x: torch.Tensor,
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -137,7 +151,7 @@ class FusedBNReLU(nn.Module):
             return _FusedBNFunction.apply(
                 x, res, self.weight, self.bias, self.running_mean,
                 self.running_var, self.momentum, self.eps, self.relu,
-                self.training)
+                self.training, self._tickets(x.device))
         # reference fallback (CPU tests / unsupported shapes)
         out = F.batch_norm(x, self.running_mean, self.running_var,
                            self.weight, self.bias, self.training,

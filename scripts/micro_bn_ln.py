@@ -35,15 +35,27 @@ def timed(label, fn, traffic_bytes):
              traffic_bytes / 1e6), flush=True)
 
 
-def bench_bn(N, C, H, W):
+# the distinct BatchNorm shapes of ResNet-50 at batch 64 (N, C, H, W)
+RESNET50_B64_BN = [
+    (64, 64, 112, 112), (64, 256, 56, 56), (64, 128, 56, 56),
+    (64, 512, 28, 28), (64, 64, 56, 56), (64, 256, 28, 28),
+    (64, 1024, 14, 14), (64, 128, 28, 28), (64, 512, 14, 14),
+    (64, 2048, 7, 7), (64, 256, 14, 14), (64, 512, 7, 7),
+]
+
+
+def bench_bn(N, C, H, W, apply=True):
     M = N * H * W
     x = torch.randn(N * H * W * C, device="cuda").to(torch.bfloat16)
     y = torch.empty_like(x)
     dy = torch.randn_like(x)
     dx = torch.empty_like(x)
     mask = torch.empty(M * C // 8, dtype=torch.uint8, device="cuda")
-    nb = core.BN_RED_BLOCKS
-    partial = torch.empty(nb * 2 * C, device="cuda")
+    ws = torch.empty(max(core.bn_stats_ws(M, C, 0), core.bn_stats_ws(M, C, 1)),
+                     device="cuda")
+    tickets = torch.zeros(2 * core.BN_TICKET_WORDS, dtype=torch.int32,
+                          device="cuda")
+    bwd_tickets = tickets.data_ptr() + 4 * core.BN_TICKET_WORDS
     mean = torch.empty(C, device="cuda")
     invstd = torch.empty(C, device="cuda")
     rm = torch.zeros(C, device="cuda")
@@ -55,31 +67,37 @@ def bench_bn(N, C, H, W):
     nbytes = M * C * 2
     tag = "bn[%d,%d,%d,%d]" % (N, C, H, W)
 
-    timed(tag + " fwd_reduce",
-          lambda: core.bn_reduce(x.data_ptr(), M, C, partial.data_ptr(), st),
+    timed(tag + " fwd_stats",
+          lambda: core.bn_fwd_stats(x.data_ptr(), M, C, 1e-5, 0.1,
+                                    mean.data_ptr(), invstd.data_ptr(),
+                                    rm.data_ptr(), rv.data_ptr(), 1,
+                                    ws.data_ptr(), tickets.data_ptr(), st),
           nbytes)
-    core.bn_finalize(partial.data_ptr(), M, C, 1e-5, 0.1, mean.data_ptr(),
-                     invstd.data_ptr(), rm.data_ptr(), rv.data_ptr(), 1, st)
-    timed(tag + " fwd_apply(+res,relu)",
-          lambda: core.bn_fwd_apply(x.data_ptr(), x.data_ptr(), y.data_ptr(),
-                                    M, C, mean.data_ptr(), invstd.data_ptr(),
-                                    g.data_ptr(), b.data_ptr(), 1,
-                                    mask.data_ptr(), st),
-          nbytes * 3)
-    timed(tag + " bwd_reduce",
-          lambda: core.bn_bwd_reduce(x.data_ptr(), dy.data_ptr(),
-                                     mask.data_ptr(), M, C, mean.data_ptr(),
-                                     invstd.data_ptr(), partial.data_ptr(),
-                                     1, st),
-          nbytes * 2)
-    core.bn_fold(partial.data_ptr(), M, C, sums2.data_ptr(), st)
-    timed(tag + " bwd_apply(+dres,relu)",
-          lambda: core.bn_bwd_apply(x.data_ptr(), dy.data_ptr(),
-                                    mask.data_ptr(), dx.data_ptr(),
-                                    y.data_ptr(), M, C, mean.data_ptr(),
-                                    invstd.data_ptr(), g.data_ptr(),
-                                    sums2.data_ptr(), 1, st),
-          nbytes * 4)
+    core.bn_fwd_apply(x.data_ptr(), x.data_ptr(), y.data_ptr(), M, C,
+                      mean.data_ptr(), invstd.data_ptr(), g.data_ptr(),
+                      b.data_ptr(), 1, mask.data_ptr(), st)
+    if apply:
+        timed(tag + " fwd_apply(+res,relu)",
+              lambda: core.bn_fwd_apply(x.data_ptr(), x.data_ptr(),
+                                        y.data_ptr(), M, C, mean.data_ptr(),
+                                        invstd.data_ptr(), g.data_ptr(),
+                                        b.data_ptr(), 1, mask.data_ptr(), st),
+              nbytes * 3)
+    # bwd statistics read x, dy and the 1-byte-per-8-channels ReLU mask
+    timed(tag + " bwd_stats(relu)",
+          lambda: core.bn_bwd_stats(x.data_ptr(), dy.data_ptr(),
+                                    mask.data_ptr(), M, C, mean.data_ptr(),
+                                    invstd.data_ptr(), sums2.data_ptr(), 1,
+                                    ws.data_ptr(), bwd_tickets, st),
+          nbytes * 2 + M * C // 8)
+    if apply:
+        timed(tag + " bwd_apply(+dres,relu)",
+              lambda: core.bn_bwd_apply(x.data_ptr(), dy.data_ptr(),
+                                        mask.data_ptr(), dx.data_ptr(),
+                                        y.data_ptr(), M, C, mean.data_ptr(),
+                                        invstd.data_ptr(), g.data_ptr(),
+                                        sums2.data_ptr(), 1, st),
+              nbytes * 4)
 
 
 def bench_ln(M, C):
@@ -109,7 +127,9 @@ def bench_ln(M, C):
 
 
 if __name__ == "__main__":
-    bench_bn(64, 64, 112, 112)     # ResNet-50 stem
-    bench_bn(64, 256, 56, 56)      # layer1 width
-    bench_bn(64, 2048, 7, 7)       # layer4 width
-    bench_ln(64 * 128, 1024)       # BERT-large b64 s128
+    # --stats: only the statistics kernels, at every ResNet-50 b64 shape
+    stats_only = "--stats" in sys.argv
+    for shape in RESNET50_B64_BN:
+        bench_bn(*shape, apply=not stats_only)
+    if not stats_only:
+        bench_ln(64 * 128, 1024)       # BERT-large b64 s128
